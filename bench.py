@@ -1,6 +1,7 @@
 """Device-resident packet-path benchmark (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config parse64|...] [--only]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config parse64|...]
+                    [--dump-outputs DIR] [--full [--only] [--no-cpu]]
 
 A step is one pass of the hot path over one batch of synthetic packets that
 is already resident in HBM.  Default workload = BASELINE config 2 with the
@@ -20,10 +21,18 @@ a gloo process group carries only the barriers, the max-over-ranks of the
 elapsed time and the per-rank figures.  value = packets processed by all
 ranks / that time.
 
+A plain run sets up, warms up, times the K steps of the --config and prints
+the line with `value` and `roofline`; everything else the benchmark measures
+rides behind --full.  --dump-outputs DIR writes what the last timed step
+computed (the arrays a caller of the timed launch receives) as DIR/<name>.npy
+after the timed steps; the inputs are seeded, so two builds of the library
+can be compared output for output.
+
 Rank 0 prints ONE JSON line:
   value / roofline    the --config (default parse64) on every rank; roofline
                       per launch from HIP events on the launch stream, with
                       each rank's fraction in roofline.per_rank;
+ with --full, also:
   shards              BASELINE config 5: IMIX parse + hash, one shard per GPU,
                       aggregate Mpps and per-rank roofline fraction (every N);
   sizes               N=1 only: the metric's other frame sizes (256 B, 1500 B)
@@ -367,7 +376,52 @@ def pmc_traffic(cfg):
     return None
 
 
-def bench_config(cfg, g, ctx, dev, steps, warmup, w=None, queues=1, n_pkts=1 << 20):
+DUMP_BUDGET = 64 << 20  # bytes of --dump-outputs files, all arrays together
+
+
+def dump_outputs(path, arrays, rank=0, world=1):
+    """Write the last timed step's outputs as <path>/<name>.npy (ranks past
+    the first of a multi-GPU run: <name>.rank<r>.npy).  Every array is
+    integer data: u8 / u16 go out as float32 and u32 as float64, both exact;
+    a 64-bit array goes out as its two 32-bit halves (<name>_lo, <name>_hi).
+    An array over its share of DUMP_BUDGET is cut to a fixed, seeded sample
+    of its elements (the same indices on every run, in index order)."""
+    path = pathlib.Path(path)
+    path.mkdir(parents=True, exist_ok=True)
+    flat = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a).reshape(-1)
+        if a.dtype.itemsize == 8:
+            u = a.view(np.uint64)
+            flat[name + "_lo"], flat[name + "_hi"] = u & 0xFFFFFFFF, u >> 32
+        else:
+            flat[name] = a.view(f"u{a.dtype.itemsize}")
+    share = DUMP_BUDGET // len(flat) - 128  # (the .npy header)
+    for k, (name, a) in enumerate(flat.items()):
+        ft = np.float32 if a.dtype.itemsize <= 2 else np.float64
+        cap = share // np.dtype(ft).itemsize
+        if a.size > cap:
+            a = a[np.sort(np.random.default_rng(0xD0 + k).integers(0, a.size, cap))]
+        np.save(path / (f"{name}.npy" if world == 1 else f"{name}.rank{rank}.npy"), a.astype(ft))
+
+
+def launcher_outputs(launcher):
+    """What a caller of the timed launch receives: the launcher's output
+    tensors (the frames too where the call rewrites them in place)."""
+    from capsule_amd import packets
+
+    if isinstance(launcher, packets.ParseLauncher):
+        out = launcher._keep[1]
+        t = {"meta": out.meta, "csum": out.csum, "flow_hash": out.flow_hash}
+    elif isinstance(launcher, packets.ReconcileLauncher):
+        t = {"arena": launcher._keep[0].arena, "status": launcher._keep[2]}
+    else:
+        arena, _, out_len, disp, status = launcher._keep[2]
+        t = {"out_arena": arena, "out_len": out_len, "disposition": disp, "status": status}
+    return {k: v.cpu().numpy() for k, v in t.items() if v is not None}
+
+
+def bench_config(cfg, g, ctx, dev, steps, warmup, w=None, queues=1, n_pkts=1 << 20, dump=None):
     """Time one config on this rank.
 
     Builds the rank's shard of the workload, keeps R copies resident in HBM
@@ -389,7 +443,7 @@ def bench_config(cfg, g, ctx, dev, steps, warmup, w=None, queues=1, n_pkts=1 << 
     w = w or make_workload(cfg, g.shard_seed(0xC0FFEE + SEEDS[cfg]), n=n_pkts)
     n = len(w["off"])
     if w["kind"] == "nat64_cold":
-        return bench_nat64_cold(cfg, g, ctx, dev, steps, warmup, w)
+        return bench_nat64_cold(cfg, g, ctx, dev, steps, warmup, w, dump)
     gw = nat64_4to6_setup(w, ctx, dev) if w["kind"] == "nat64_4to6" else None
     meta_d = reconcile_setup(w, ctx, dev) if w["kind"] == "reconcile" else None
     batch_bytes = len(w["arena"]) + 6 * n
@@ -415,12 +469,14 @@ def bench_config(cfg, g, ctx, dev, steps, warmup, w=None, queues=1, n_pkts=1 << 
         gw = gw or packets.Nat64Gateway(ctx, capacity_log2=PORTMAP_LOG2)
         if "out_off" in w:
             oo = torch.from_numpy(w["out_off"].view(np.int32)).to(dev)
-            outs = [(torch.empty(w["out_size"], dtype=torch.uint8, device=dev), oo,
+            # (arenas zeroed once: the bytes between the output frames, which no
+            # launch writes, are the same from run to run for --dump-outputs)
+            outs = [(torch.zeros(w["out_size"], dtype=torch.uint8, device=dev), oo,
                      torch.empty(n, dtype=torch.int16, device=dev),
                      torch.empty(n, dtype=torch.uint8, device=dev),
                      torch.empty(n, dtype=torch.uint8, device=dev)) for _ in range(2)]
         else:
-            outs = [(torch.empty_like(b.arena), b.off, torch.empty(n, dtype=torch.int16, device=dev),
+            outs = [(torch.zeros_like(b.arena), b.off, torch.empty(n, dtype=torch.int16, device=dev),
                      torch.empty(n, dtype=torch.uint8, device=dev),
                      torch.empty(n, dtype=torch.uint8, device=dev)) for b in batches[:2]]
         launchers = [packets.Nat64Launcher(gw, batches[k % copies], outs[k & 1], stream,
@@ -482,6 +538,8 @@ def bench_config(cfg, g, ctx, dev, steps, warmup, w=None, queues=1, n_pkts=1 << 
                steps=steps, kern_us=kern_us, algo_bytes=w["algo_bytes"],
                achieved=w["algo_bytes"] / (kern_us * 1e-6) / 1e9, w=w,
                line_floor=w.get("line_floor"))
+    if dump:  # the outputs of the last timed launch
+        dump_outputs(dump, launcher_outputs(launchers[(state["k"] - 1) % cycle]), g.rank, g.world)
     del launchers, outs, batches, b0
     if gw is not None:
         gw.close()
@@ -544,7 +602,7 @@ def check_devices(devs, one_device):
                          "to rehearse N ranks on one device")
 
 
-def bench_nat64_cold(cfg, g, ctx, dev, steps, warmup, w):
+def bench_nat64_cold(cfg, g, ctx, dev, steps, warmup, w, dump=None):
     """The cold port map: every timed call is the first pass of the stream
     over a freshly reset map (cgpu_portmap_reset, enqueued on the stream
     before the call), so every key is new and its port comes from the
@@ -562,7 +620,7 @@ def bench_nat64_cold(cfg, g, ctx, dev, steps, warmup, w):
     gw = packets.Nat64Gateway(ctx, capacity_log2=PORTMAP_LOG2)
     b = packets.PacketBatch.from_numpy(w["arena"], w["off"], w["len"], dev)
     oo = torch.from_numpy(w["out_off"].view(np.int32)).to(dev)
-    out = (torch.empty(w["out_size"], dtype=torch.uint8, device=dev), oo,
+    out = (torch.zeros(w["out_size"], dtype=torch.uint8, device=dev), oo,
            torch.empty(n, dtype=torch.int16, device=dev),
            torch.empty(n, dtype=torch.uint8, device=dev),
            torch.empty(n, dtype=torch.uint8, device=dev))
@@ -591,6 +649,8 @@ def bench_nat64_cold(cfg, g, ctx, dev, steps, warmup, w):
     elapsed = g.timed(one, steps, sync=lambda: torch.cuda.synchronize(dev))
     kern_us = sum(a.elapsed_time(z) for a, z in evs) / steps * 1e3
     keys = gw.size()
+    if dump:
+        dump_outputs(dump, launcher_outputs(launch), g.rank, g.world)
     gw.close()
     del launch, out, b
     torch.cuda.synchronize(dev)
@@ -684,10 +744,17 @@ def main():
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--config", default="parse64", choices=list(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="after the --config's timed steps, also time the `shards`, `sizes` and "
+                         "`rx_queues` objects and the CPU baseline (a plain run does none of "
+                         "these: it is --full --only --no-cpu)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the outputs of the last timed launch of "
+                         "the --config as DIR/<name>.npy (float32 / float64, at most 64 MB)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: no CPU baseline")
     ap.add_argument("--only", action="store_true",
-                    help="time the --config only (no `shards` / `sizes` objects; for profiling)")
+                    help="with --full: time the --config only (no `shards` / `sizes` objects)")
     ap.add_argument("--sub-steps", type=int, default=300,
                     help="timed launches of each `shards` / `sizes` config (at least --steps)")
     ap.add_argument("--n", type=int, default=1 << 20,
@@ -706,6 +773,10 @@ def main():
                     help="with --ingress frames: bursts in flight (2: cgpu_parse_frames_submit "
                          "/ _wait, the next burst submitted before the previous one is waited for)")
     args = ap.parse_args()
+    if not args.full:  # the plain run: the --config's timed steps and its line
+        args.only = args.no_cpu = True
+    if args.dump_outputs and (args.e2e or args.stub):
+        raise SystemExit("--dump-outputs applies to the device-resident run")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # Not started by torch.distributed.run: start one rank process per GPU
@@ -745,7 +816,8 @@ def main():
     check_devices(DEVICES, one_device)
     ctx = packets.Context(ordinal)
 
-    main_r = bench_config(args.config, g, ctx, dev, args.steps, args.warmup, n_pkts=args.n)
+    main_r = bench_config(args.config, g, ctx, dev, args.steps, args.warmup, n_pkts=args.n,
+                          dump=args.dump_outputs)
     extra = {}
     if not args.only:
         sub = max(args.steps, args.sub_steps)

@@ -1,6 +1,6 @@
 #!/bin/bash
-# GPU-box validation: smoke, GPU tests, the default bench and the driver's
-# short bench.  Each GPU step has its own time limit; a failure stops the
+# GPU validation: smoke, GPU tests, the driver's short plain bench and the
+# full bench line (--full).  Each GPU step has its own time limit; a failure stops the
 # script (rc 1 = test failures, still reported; >= 124 or a signal = stop).
 export TMPDIR=/tmp
 mkdir -p gpurun_out
@@ -15,4 +15,4 @@ step() {  # name, limit, command...
 step smoke 400 python -c "import __graft_entry__ as g; g.smoke()"
 step pytest_gpu 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread
 step bench_driver 400 python bench.py --gpus 1 --steps 20 --warmup 5
-step bench_default 400 python bench.py
+step bench_full 400 python bench.py --full

@@ -75,7 +75,7 @@ def test_bench_launcher_spawns_n_ranks():
     """`bench.py --gpus 2` without torch.distributed.run starts two rank
     processes itself (GPU-free worker stub here) and reports both."""
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--stub", "--steps", "3",
-                        "--warmup", "1"], capture_output=True, text=True, timeout=300,
+                        "--warmup", "1", "--full"], capture_output=True, text=True, timeout=300,
                        env=_stub_env(), cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _bench_line(r.stdout)
@@ -100,17 +100,35 @@ def test_bench_under_torchrun_stub():
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
                         "--nproc-per-node=2", "--master-addr=127.0.0.1",
                         f"--master-port={port}", "bench.py", "--gpus", "2", "--stub",
-                        "--steps", "3", "--warmup", "1"],
+                        "--steps", "3", "--warmup", "1", "--full"],
                        capture_output=True, text=True, timeout=300, env=_stub_env(), cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _bench_line(r.stdout)
     assert d["n_gpus"] == 2 and len(d["shards"]["per_rank"]) == 2
 
 
+def test_bench_plain_line_shape():
+    """A plain run (no --full): the metric line of the --config alone, with
+    --steps timed steps and none of the objects that take runs of their own."""
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--stub", "--steps", "3",
+                        "--warmup", "1"],
+                       capture_output=True, text=True, timeout=300, env=_stub_env(), cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = _bench_line(r.stdout)
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1
+    assert d["unit"] == "Mpps" and d["higher_is_better"] is True and d["dtype"] == "u8"
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and "roofline" in d
+    # value = packets of the timed steps / their time; ms_per_step = that time / steps
+    pkts = d["config"]["packets_per_step"]
+    assert abs(d["value"] * d["ms_per_step"] / (pkts / 1e3) - 1) < 0.02
+    assert not {"shards", "sizes", "rx_queues", "cpu_baseline"} & set(d)
+
+
 def test_bench_single_gpu_line_shape():
-    """N=1: the metric line plus `shards` (config 5 at N=1) and `sizes`
+    """N=1, --full: the metric line plus `shards` (config 5 at N=1) and `sizes`
     (the metric's other sizes and configs 3/3'/4)."""
-    r = subprocess.run([sys.executable, "bench.py", "--stub", "--steps", "2", "--warmup", "1"],
+    r = subprocess.run([sys.executable, "bench.py", "--stub", "--steps", "2", "--warmup", "1",
+                        "--full"],
                        capture_output=True, text=True, timeout=300, env=_stub_env(), cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _bench_line(r.stdout)
@@ -139,7 +157,7 @@ def test_bench_eight_ranks_stub():
     """The driver's 8-GPU line shape: 8 rank processes, one row per rank with
     its own device (distinct PCI addresses), n_gpus 8."""
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "8", "--stub", "--steps", "2",
-                        "--warmup", "1"], capture_output=True, text=True, timeout=600,
+                        "--warmup", "1", "--full"], capture_output=True, text=True, timeout=600,
                        env=_stub_env(), cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _bench_line(r.stdout)
