@@ -139,6 +139,33 @@ EXPORTS = [
     "cgpu_ctx_check", "cgpu_parse_frames_submit", "cgpu_parse_frames_wait",
 ]
 
+# The transmit-side extension, include/capsule_gpu_tx.h (checked by
+# tests/test_abi_tx.py): separately versioned, same library.
+TX_ABI_VERSION = 1
+TX_EXPORTS = ["cgtx_build_batch", "cgtx_hdr_defaults", "cgtx_build_status_str", "cgtx_abi_version"]
+BUILD_STATUS = ["OK", "BAD_RECORD", "NO_ROOM", "BAD_PAYLOAD"]
+BUILD = {name: i for i, name in enumerate(BUILD_STATUS)}
+
+
+class TxPayload(ctypes.Structure):  # cgtx_payload
+    _fields_ = [
+        ("arena", ctypes.c_void_p),
+        ("arena_len", ctypes.c_uint64),
+        ("off", ctypes.c_void_p),
+        ("len", ctypes.c_void_p),
+    ]
+
+
+class TxFramesOut(ctypes.Structure):  # cgtx_frames_out
+    _fields_ = [
+        ("arena", ctypes.c_void_p),
+        ("arena_len", ctypes.c_uint64),
+        ("off", ctypes.c_void_p),
+        ("len", ctypes.c_void_p),
+        ("status", ctypes.c_void_p),
+    ]
+
+
 _libs = {}
 
 
@@ -209,7 +236,14 @@ def lib(test=False):
     L.cgpu_reconcile.argtypes = [vp, vp, ctypes.c_uint64, vp, vp, vp, u32, u32, u32, vp, vp]
     L.cgpu_reconcile_frames.restype = i32
     L.cgpu_reconcile_frames.argtypes = [vp, vp, vp, vp, u32, u32, u32, vp]
-    if L.cgpu_abi_version() != ABI_VERSION:
+    L.cgtx_abi_version.restype = i32
+    L.cgtx_build_status_str.restype = ctypes.c_char_p
+    L.cgtx_build_status_str.argtypes = [i32]
+    L.cgtx_hdr_defaults.restype = i32
+    L.cgtx_hdr_defaults.argtypes = [u32, u32, vp]
+    L.cgtx_build_batch.restype = i32
+    L.cgtx_build_batch.argtypes = [vp, vp, u32, P(TxPayload), P(TxFramesOut), u32, vp]
+    if L.cgpu_abi_version() != ABI_VERSION or L.cgtx_abi_version() != TX_ABI_VERSION:
         raise RuntimeError(f"capsule_amd: {path.name} ABI version mismatch")
     _libs[test] = L
     return L

@@ -533,3 +533,102 @@ class Send(Batch):
         """Drain the source."""
         while self.run_once():
             pass
+
+
+# ---- sources and replacements that build frames on the device ---------------
+class PollFn(Poll):
+    """`batch::poll_fn(f)` (batch/poll.rs:56-62): a source whose bursts come
+    from a function (each call returns a PacketBatch or a list of frames; an
+    empty burst ends the replenish)."""
+
+    def __init__(self, ctx, fn, device="cuda:0", target=1):
+        if not callable(fn):
+            raise TypeError("PollFn takes a function returning a burst")
+        super().__init__(ctx, fn, device, target)
+
+
+class syn_flood:
+    """The source of examples/syn-flood/main.rs:43-69 as a function for
+    `PollFn`: every call is one `Mbuf::alloc_bulk(n)` burst run through the
+    `map` closure -- Ethernet (src_mac, dst 02:00:00:ff:ff:ff), Ipv4 (src =
+    next_ip after `next_ip += 1`, dst 10.100.1.255), Tcp4 (SYN, seq_no 1,
+    window 10, dst_port 80), reconcile_all -- built by one
+    packets.build call.  `next_ip` starts at 10.0.0.0 and carries on across
+    bursts (wrapping like the reference's u32)."""
+
+    def __init__(self, ctx, n=128, src_mac=b"\x02\x00\x00\x00\x00\x01",
+                 dst_mac=b"\x02\x00\x00\xff\xff\xff", dst_ip=bytes([10, 100, 1, 255]),
+                 next_ip=10 << 24, device="cuda:0"):
+        self.ctx, self.n, self.next_ip, self.device = ctx, n, next_ip, device
+        rec = packets.default_records(n, 4, "tcp", device)
+        packets.record_set(rec, "src_mac", bytes(src_mac))
+        packets.record_set(rec, "dst_mac", bytes(dst_mac))
+        packets.record_set(rec, "dst_ip", bytes(dst_ip))
+        packets.record_set(rec, "tcp_flags", 0x02)  # set_syn
+        packets.record_set(rec, "seq_no", 1)
+        packets.record_set(rec, "udp_length_or_window", 10)
+        packets.record_set(rec, "dst_port", 80)
+        self.records = rec
+        self.last_status = None
+
+    def __call__(self):
+        ip = (torch.arange(1, self.n + 1, device=self.device, dtype=torch.int64) + self.next_ip) & 0xFFFFFFFF
+        self.next_ip = (self.next_ip + self.n) & 0xFFFFFFFF
+        rec = self.records.clone()
+        # the address in wire order: the big-endian bytes of the u32
+        rec[:, 40:44] = torch.stack([(ip >> s) & 0xFF for s in (24, 16, 8, 0)], dim=1).to(torch.uint8)
+        frames, self.last_status = packets.build(self.ctx, rec)
+        return frames
+
+
+_REC = packets._REC_DTYPE.fields
+
+
+def echo_reply_v4(ctx, room=2048):
+    """`reply_echo` of examples/ping4d/main.rs:29-54 as a function for
+    `.replace(...)` behind `.parse(F_ACCEPT_V4 | F_ACCEPT_ICMP, fields=True)`,
+    entirely on the device: the reply records are made from the parsed ones
+    with tensor ops (MACs and addresses swapped, ttl 255, everything else at
+    its default, msg_type 0), the payload is the request's own bytes from its
+    L4 offset + 4 (identifier, sequence number, data) to data_len, and one
+    packets.build call makes the frames.
+
+    A packet that is not ICMPv4, or whose type is not 8, aborts with
+    NOT_ICMPV4: the reference's `peek::<EchoRequest>()` error "the ICMPv4
+    packet is not EchoRequest" has no status code of its own.  A request with
+    fewer than 4 body bytes aborts as the body's read_data would
+    (mbuf.rs:313-327): L4_BAD_OFFSET with none, L4_OUT_OF_BUFFER with 1-3."""
+
+    def fn(sub):
+        r = sub.parsed
+        if r is None or r.fields is None:
+            raise ValueError("echo_reply_v4 needs .parse(..., fields=True) upstream")
+        f, meta = r.fields, r.meta
+        dev = f.device
+        n = sub.n
+        icmp4 = (((meta >> 16) & 3) == N.L3_IPV4) & (((meta >> 18) & 3) == N.L4_ICMP)
+        so = _REC["src_port"][1]
+        mtype = f[:, so].to(torch.int32) | (f[:, so + 1].to(torch.int32) << 8)
+        l4 = ((meta >> 8) & 0xFF) + 20
+        body = (sub.batch.len.to(torch.int32) & 0xFFFF) - l4 - 4
+        st = torch.zeros(n, dtype=torch.uint8, device=dev)
+        st[(body >= 1) & (body <= 3)] = N.PKT["L4_OUT_OF_BUFFER"]
+        st[body <= 0] = N.PKT["L4_BAD_OFFSET"]
+        st[~(icmp4 & (mtype == 8))] = N.PKT["NOT_ICMPV4"]
+        rec = packets.default_records(n, 4, "icmp", dev)
+        for dst, src in (("src_mac", "dst_mac"), ("dst_mac", "src_mac"), ("src_ip", "dst_ip"),
+                         ("dst_ip", "src_ip")):
+            (dt, do), (_, s0) = _REC[dst][:2], _REC[src][:2]
+            rec[:, do:do + dt.itemsize] = f[:, s0:s0 + dt.itemsize]
+        packets.record_set(rec, "ttl", 255)
+        packets.record_set(rec, "src_port", 0)  # EchoReply
+        good = st == 0
+        poff = _u32_to_i32((sub.batch.off.long() & 0xFFFFFFFF) + l4 + 4)
+        plen = torch.where(good, body, torch.zeros_like(body)).to(torch.int16)
+        pay = packets.PacketBatch(sub.batch.arena, torch.where(good, poff, torch.zeros_like(poff)), plen)
+        frames, bst = packets.build(ctx, rec, payload=pay, room=room)
+        # Mbuf::extend's NotResized when the reply does not fit the data room
+        st = torch.where(good & (bst != N.BUILD["OK"]), torch.full_like(st, N.PKT["NOT_RESIZED"]), st)
+        return frames, st
+
+    return fn

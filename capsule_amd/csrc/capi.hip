@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "capsule_gpu.h"
+#include "capsule_gpu_tx.h"
 #include "kernels.hpp"
 
 // How a nat64 call orders itself behind the map's previous call: it waits
@@ -1779,6 +1780,68 @@ int cgpu_reconcile_frames(cgpu_ctx *ctx, uint8_t *const *frames, const uint16_t 
     for (uint32_t i = 0; i < n; ++i) status[i] = H[o_st + fill[region[i]]++];
   }
   if (int e = sync_done(ctx)) return fail(e);
+  return ok();
+}
+
+// ---- transmit-side extension (include/capsule_gpu_tx.h) --------------------
+int cgtx_abi_version(void) { return CGTX_ABI_VERSION; }
+
+const char *cgtx_build_status_str(int s) {
+  switch (s) {
+    case CGTX_BUILD_OK: return "ok";
+    case CGTX_BUILD_BAD_RECORD: return "record names no push chain";
+    case CGTX_BUILD_NO_ROOM: return "buffer not resized";
+    case CGTX_BUILD_BAD_PAYLOAD: return "payload out of its arena";
+    default: return "unknown status";
+  }
+}
+
+static bool tx_chain(uint32_t version, uint32_t protocol) {
+  if (version != 4u && version != 6u) return false;
+  return protocol == 17u || protocol == 6u || protocol == (version == 4u ? 1u : 58u);
+}
+
+int cgtx_hdr_defaults(uint32_t version, uint32_t protocol, cgpu_hdr_record *rec) {
+  if (!rec || !tx_chain(version, protocol)) return fail(CGPU_EINVAL);
+  memset(rec, 0, sizeof *rec);
+  rec->version = (uint8_t)version;
+  rec->ihl = version == 4u ? 5u : 0u;  // Ipv4Header::default: version_ihl 0x45
+  rec->ttl = 64;                       // DEFAULT_IP_TTL (ip/mod.rs:33)
+  rec->protocol = (uint8_t)protocol;
+  if (protocol == 6u) rec->data_offset = 5;  // TcpHeader::default: 5 << 4
+  return ok();
+}
+
+int cgtx_build_batch(cgpu_ctx *ctx, const cgpu_hdr_record *rec, uint32_t n,
+                     const cgtx_payload *pay, const cgtx_frames_out *out, uint32_t room,
+                     void *stream) {
+  if (!ctx || !rec || !out || !out->arena || !out->off || !out->len) return fail(CGPU_EINVAL);
+  if (n > CGPU_MAX_BATCH || room == 0u || room > 65536u) return fail(CGPU_EINVAL);
+  if (out->arena_len > 0xffff0000ull) return fail(CGPU_EINVAL);
+  const bool has_pay = pay && pay->arena;
+  if (has_pay) {
+    if (!pay->off || !pay->len || pay->arena_len > 0xffff0000ull) return fail(CGPU_EINVAL);
+    const uintptr_t o = (uintptr_t)out->arena, p = (uintptr_t)pay->arena;
+    if (o < p + pay->arena_len && p < o + out->arena_len) return fail(CGPU_EINVAL);
+  }
+  if (n == 0) return ok();
+  DeviceGuard dg(ctx->device);
+  if (!dg.ok()) return fail(CGPU_ENODEV);
+  cgpu::BuildArgs a{};
+  a.rec = rec;
+  a.n = n;
+  a.pay_arena = has_pay ? pay->arena : nullptr;
+  a.pay_len = has_pay ? (uint32_t)pay->arena_len : 0u;
+  a.pay_off = has_pay ? pay->off : nullptr;
+  a.pay_plen = has_pay ? pay->len : nullptr;
+  a.out_arena = out->arena;
+  a.out_arena_len = (uint32_t)out->arena_len;
+  a.out_off = out->off;
+  a.out_len = out->len;
+  a.status = out->status;
+  a.room = room;
+  hipError_t e = cgpu::launch_build(a, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e);
   return ok();
 }
 

@@ -226,4 +226,21 @@ struct SetIpArgs {
 };
 hipError_t launch_set_ip(const SetIpArgs &a, hipStream_t s);
 
+// ---- cgtx_build_batch (build.hip) ------------------------------------------
+struct BuildArgs {
+  const cgpu_hdr_record *rec;
+  uint32_t n;
+  const uint8_t *pay_arena;  // nullptr: no payloads (pay_len 0)
+  uint32_t pay_len;
+  const uint32_t *pay_off;
+  const uint16_t *pay_plen;
+  uint8_t *out_arena;
+  uint32_t out_arena_len;
+  const uint32_t *out_off;
+  uint16_t *out_len;
+  uint8_t *status;  // optional
+  uint32_t room;    // data room of Mbuf::extend's tailroom model (mbuf.rs:225-233)
+};
+hipError_t launch_build(const BuildArgs &a, hipStream_t s);
+
 }  // namespace cgpu

@@ -687,3 +687,104 @@ class Nat64Launcher:
         rc = self._fn(*self._args)
         if rc:
             N.check(rc, self._name)
+
+
+# ---- construction: include/capsule_gpu_tx.h ---------------------------------
+_REC_DTYPE = np.dtype(N.HDR_RECORD_FIELDS)
+_L3 = {4: 4, 6: 6, "v4": 4, "v6": 6, "ipv4": 4, "ipv6": 6}
+_L4 = {"udp": 17, "tcp": 6, "icmp": None, 17: 17, 6: 6, 1: None, 58: None}
+MAX_HEADER = 74  # Ethernet + Ipv6 + Tcp, the longest chain build() pushes
+
+
+def hdr_defaults(l3, l4):
+    """`cgtx_hdr_defaults` -> one numpy record: the reference's Default
+    impls of the chain (ttl 64, ihl 5 under IPv4, data_offset 5 for TCP)."""
+    version = _L3[l3]
+    proto = _L4[l4] or (1 if version == 4 else 58)
+    rec = np.zeros(1, _REC_DTYPE)
+    N.check(N.lib().cgtx_hdr_defaults(version, proto, rec.ctypes.data), "cgtx_hdr_defaults")
+    return rec
+
+
+def default_records(n, l3, l4, device):
+    """n default header records of the chain (l3: 4 / 6, l4: "udp" / "tcp" /
+    "icmp") as a device uint8 [n, 96] tensor, to be filled with `record_set`
+    and handed to `build`."""
+    one = torch.from_numpy(hdr_defaults(l3, l4).view(np.uint8).reshape(1, N.HDR_RECORD_SIZE))
+    return one.to(device).repeat(n, 1)
+
+
+def record_set(records, name, value):
+    """Set field `name` of every record (device uint8 [n, 96]) with tensor
+    ops: `value` is an int, a bytes-like (array fields: MACs, addresses), an
+    integer tensor [n] (stored little-endian, as the record holds it) or a
+    uint8 tensor [n, k] (array fields, wire order)."""
+    dt, off = _REC_DTYPE.fields[name][:2]
+    size = dt.itemsize
+    col = records[:, off:off + size]
+    if isinstance(value, (bytes, bytearray)):
+        value = torch.tensor(list(value), dtype=torch.uint8, device=records.device)
+    if isinstance(value, torch.Tensor) and value.dtype == torch.uint8 and value.dim() >= 1 and dt.shape:
+        col[:, : value.shape[-1]] = value
+        return records
+    if isinstance(value, torch.Tensor):
+        v = value.to(torch.int64)
+        for b in range(size):
+            col[:, b] = ((v >> (8 * b)) & 0xFF).to(torch.uint8)
+    else:
+        for b in range(size):
+            col[:, b] = (int(value) >> (8 * b)) & 0xFF
+    return records
+
+
+def build(ctx, records, payload=None, out_arena=None, out_off=None, room=2048, slot=None,
+          stream=None):
+    """`cgtx_build_batch`: one frame per header record -- `Mbuf::new()`,
+    `push::<Ethernet>()`, `push::<Ipv4|Ipv6>()`, `push::<Udp|Tcp|echo>()`, the
+    setters, the payload, `reconcile_all()` -- in one launch.
+
+    records: device uint8 [n, 96] (`default_records`, or a parse's fields).
+    payload: a PacketBatch naming each packet's payload bytes (arena, off,
+    len), or None.  Frame i goes to out_off[i] of out_arena; without out_off
+    the frames are laid out in `slot`-byte slots (default: the next multiple
+    of 64 above the longest frame possible: the 74-B header without payloads,
+    room - 1 with).  room: the mbuf data room of Mbuf::extend (a frame is
+    built only if frame_len < room).  Returns (PacketBatch, status u8 [n],
+    N.BUILD); a packet that is not built has len 0.  Asynchronous on
+    `stream`."""
+    if records.dtype != torch.uint8 or records.numel() % N.HDR_RECORD_SIZE:
+        raise TypeError("build takes cgpu_hdr_record records (uint8 [n, 96])")
+    records = records.contiguous()
+    n = records.numel() // N.HDR_RECORD_SIZE
+    dev = records.device
+    if out_off is None:
+        if slot is None:
+            longest = MAX_HEADER if payload is None else max(MAX_HEADER, room - 1)
+            slot = (longest // 64 + 1) * 64
+        if n * slot > 0xFFFF0000:
+            raise ValueError("out arena past 4 GiB: pass out_off or a smaller slot")
+        out_off = (torch.arange(n, device=dev, dtype=torch.int64) * slot)
+        out_off = torch.where(out_off >= 1 << 31, out_off - (1 << 32), out_off).to(torch.int32)
+        if out_arena is None:
+            out_arena = torch.empty(n * slot, dtype=torch.uint8, device=dev)
+    elif out_arena is None:
+        raise ValueError("out_off needs the out_arena it indexes")
+    out_len = torch.empty(n, dtype=torch.int16, device=dev)
+    status = torch.empty(n, dtype=torch.uint8, device=dev)
+    fo = N.TxFramesOut()
+    fo.arena, fo.arena_len = out_arena.data_ptr(), out_arena.numel()
+    fo.off, fo.len, fo.status = out_off.data_ptr(), out_len.data_ptr(), status.data_ptr()
+    pay = None
+    if payload is not None:
+        if payload.n != n:
+            raise ValueError("payload: one (off, len) per record")
+        pay = N.TxPayload()
+        pay.arena, pay.arena_len = payload.arena.data_ptr(), payload.arena.numel()
+        pay.off, pay.len = payload.off.data_ptr(), payload.len.data_ptr()
+    rc = ctx.L.cgtx_build_batch(ctx.handle, _ptr(records), n,
+                                ctypes.byref(pay) if pay is not None else None,
+                                ctypes.byref(fo), room, _stream_handle(stream))
+    N.check(rc, "cgtx_build_batch")
+    if stream is not None:
+        records.record_stream(stream)
+    return PacketBatch(out_arena, out_off, out_len), status

@@ -11,13 +11,18 @@ use std::path::PathBuf;
 fn main() {
     let root = PathBuf::from(env::var("CAPSULE_GPU_ROOT").expect("CAPSULE_GPU_ROOT: the capsule_amd checkout"));
     let rocm = env::var("ROCM_PATH").unwrap_or_else(|_| "/opt/rocm".to_string());
-    let header = root.join("include").join("capsule_gpu.h");
+    // capsule_gpu_tx.h (the transmit-side extension, cgtx_*) includes
+    // capsule_gpu.h, so one header brings in both surfaces.
+    let header = root.join("include").join("capsule_gpu_tx.h");
 
     bindgen::Builder::default()
         .header(header.to_str().expect("utf-8 path"))
         .whitelist_type(r"cgpu_.*")
         .whitelist_function(r"cgpu_.*")
         .whitelist_var(r"CGPU_.*")
+        .whitelist_type(r"cgtx_.*")
+        .whitelist_function(r"cgtx_.*")
+        .whitelist_var(r"CGTX_.*")
         .derive_copy(true)
         .derive_debug(true)
         .derive_default(true)
