@@ -6,62 +6,61 @@ import pytest
 import torch
 
 import pyref_build as B
+from build_cases import CHAINS, HDR, REC, make_records, zero_checksum_record
 from capsule_amd import _native as N
 from capsule_amd import batch, packets
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
-REC = np.dtype(N.HDR_RECORD_FIELDS)
-CHAINS = ((4, 17), (4, 6), (4, 1), (6, 17), (6, 6), (6, 58))
-HDR = {(4, 17): 42, (4, 6): 54, (4, 1): 38, (6, 17): 62, (6, 6): 74, (6, 58): 58}
 
 
-def make_records(chains, rng):
-    """Records of the given chains with every settable field random."""
-    n = len(chains)
-    r = np.zeros(n, REC)
-    v = np.array([c[0] for c in chains])
-    p = np.array([c[1] for c in chains])
-    r["version"], r["protocol"] = v, p
-    r["ihl"] = np.where(v == 4, 5, 0)
-    r["dst_mac"] = rng.integers(0, 256, (n, 6))
-    r["src_mac"] = rng.integers(0, 256, (n, 6))
-    r["dscp"], r["ecn"], r["ttl"] = rng.integers(0, 64, n), rng.integers(0, 4, n), rng.integers(0, 256, n)
-    r["src_ip"] = rng.integers(0, 256, (n, 16))
-    r["dst_ip"] = rng.integers(0, 256, (n, 16))
-    r["identification"] = rng.integers(0, 65536, n)
-    r["ip_flags"], r["fragment_offset"] = rng.integers(0, 4, n), rng.integers(0, 0x2000, n)
-    r["flow_label"] = rng.integers(0, 1 << 20, n)
-    r["src_port"], r["dst_port"] = rng.integers(0, 65536, n), rng.integers(0, 65536, n)
-    icmp = (p == 1) | (p == 58)
-    pick = rng.integers(0, 2, n)
-    r["src_port"] = np.where(icmp, np.where(v == 4, np.where(pick, 8, 0), np.where(pick, 128, 129)), r["src_port"])
-    r["dst_port"] = np.where(icmp, rng.integers(0, 256, n), r["dst_port"])
-    r["seq_no"], r["ack_no"] = rng.integers(0, 1 << 32, n), rng.integers(0, 1 << 32, n)
-    r["data_offset"], r["ns"], r["tcp_flags"] = rng.integers(0, 16, n), rng.integers(0, 2, n), rng.integers(0, 256, n)
-    r["udp_length_or_window"], r["urgent_pointer"] = rng.integers(0, 65536, n), rng.integers(0, 65536, n)
-    # what the build must ignore
-    r["ether_type"], r["eth_len"], r["vlan"] = rng.integers(0, 65536, n), 18, rng.integers(0, 3, n)
-    r["ip_length"], r["ip_checksum"], r["l4_checksum"] = (rng.integers(0, 65536, n) for _ in range(3))
-    return r
+GUARD = 64  # bytes kept around an arena that is a slice of a larger tensor
 
 
-def run(ctx, recs, out_off, out_size, pay=None, room=2048):
+def sliced(size, base, fill, data=None):
+    """A device tensor of `size` bytes that starts `base` bytes above a 16-B
+    boundary, as a slice of a larger one filled with `fill` -> (whole, slice)."""
+    whole = torch.full((GUARD + 16 + size + GUARD,), fill, dtype=torch.uint8, device=DEV)
+    assert whole.data_ptr() % 16 == 0 and 0 <= base < 16
+    part = whole[GUARD + base : GUARD + base + size]
+    if data is not None:
+        part.copy_(torch.from_numpy(np.ascontiguousarray(data, dtype=np.uint8)))
+    assert part.data_ptr() % 16 == base and part.is_contiguous()
+    return whole, part
+
+
+def run(ctx, recs, out_off, out_size, pay=None, room=2048, out_base=None, pay_base=None, want=None):
     """One build call over a canary-filled arena -> (arena, len, status) as
-    numpy, and the same from pyref_build."""
+    numpy, and the same from pyref_build.  With out_base / pay_base (0..15)
+    that arena is a slice of a larger tensor and starts so many bytes above
+    a 16-B boundary: the out tensor is 0xA5 all over, and has to be outside
+    the slice afterwards too; the payload tensor is 0x3C around the slice,
+    which pyref_build, given the slice alone, never sees."""
     n = len(recs)
     rt = torch.from_numpy(recs.view(np.uint8).reshape(n, 96).copy()).to(DEV)
-    arena = torch.full((out_size,), 0xA5, dtype=torch.uint8, device=DEV)
+    if out_base is None:
+        whole = arena = torch.full((out_size,), 0xA5, dtype=torch.uint8, device=DEV)
+    else:
+        whole, arena = sliced(out_size, out_base, 0xA5)
     off = torch.from_numpy(np.asarray(out_off, np.uint32).view(np.int32)).to(DEV)
     pb = None
-    if pay is not None:
+    if pay is not None and pay_base is None:
         pb = packets.PacketBatch.from_numpy(*pay, DEV)
+    elif pay is not None:
+        pb = packets.PacketBatch.from_numpy(np.zeros(0, np.uint8), pay[1], pay[2], DEV)
+        pb = packets.PacketBatch(sliced(len(pay[0]), pay_base, 0x3C, pay[0])[1], pb.off, pb.len)
     ob, st = packets.build(ctx, rt, payload=pb, out_arena=arena, out_off=off, room=room)
     torch.cuda.synchronize()
     got = (arena.cpu().numpy(), ob.len.cpu().numpy().view(np.uint16), st.cpu().numpy())
-    want = B.build_batch(recs, out_off, out_size, *(pay if pay is not None else (None, None, None)),
-                         room=room)
+    if out_base is not None:
+        lo = GUARD + out_base
+        outside = torch.cat((whole[:lo], whole[lo + out_size :])).cpu().numpy()
+        bad = np.nonzero(outside != 0xA5)[0]
+        assert bad.size == 0, ("bytes written outside the out arena", out_base, bad[:16] - lo)
+    if want is None:  # else: what an earlier run of the same inputs returned
+        want = B.build_batch(recs, out_off, out_size, *(pay if pay is not None else (None, None, None)),
+                             room=room)
     return got, want
 
 
@@ -89,16 +88,6 @@ def test_all_chains_one_burst(ctx, n):
     got, want = run(ctx, recs, off, int(off[-1] + flen[-1]) + 9, (parena, poff, plen))
     assert (want[2] == B.OK).all() and (want[1] == flen).all()
     check(got, want)
-
-
-def zero_checksum_record():
-    """An IPv4/UDP record (no payload) whose computed checksum is 0: with
-    src_port 0 the checksum is c, so src_port = c raises the sum to 0xFFFF."""
-    r = np.zeros(1, REC)
-    r["version"], r["protocol"], r["ihl"], r["ttl"] = 4, 17, 5, 64
-    c = B.build_frame(r[0])[1][40:42]
-    r["src_port"] = (c[0] << 8) | c[1]
-    return r
 
 
 @pytest.mark.parametrize("plen", [0, 1, 2, 3, 4, 5, 15, 16, 17, 31, 32, 33, 63, 64, 65, 127, 128, 129,

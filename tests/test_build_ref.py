@@ -150,6 +150,40 @@ def test_oracle_parses_what_pyref_builds():
         assert f[14 + l3 + hl:] == pay
 
 
+def test_oracle_parses_long_pyref_frames():
+    """The same at the lengths the device tests reach: frames of 2047, 9000
+    and 65535 bytes (the longest buildable one) of every chain, room 65536."""
+    rng = np.random.default_rng(12)
+    cases = []
+    for r, _ in records()[::4]:
+        v, p = int(r["version"]), int(r["protocol"])
+        hdr = 14 + (20 if v == 4 else 40) + {17: 8, 6: 20}.get(p, 4)
+        for flen in (2047, 9000, 65535):
+            cases.append((r, bytes(rng.integers(0, 256, flen - hdr, dtype=np.uint8)), flen))
+    assert len(cases) == 18
+    frames = []
+    for r, pay, flen in cases:
+        st, f = B.build_frame(r, pay, room=65536)
+        assert st == B.OK and len(f) == flen
+        frames.append(f)
+    assert B.build_frame(cases[-1][0], cases[-1][1] + b"\0", room=65536)[0] == B.NO_ROOM
+    meta, csum, got = parse(frames)
+    for (r, pay, flen), f, m, g in zip(cases, frames, meta, got):
+        m = int(m)
+        v, p = int(r["version"]), int(r["protocol"])
+        assert N.meta_status(m) == 0 and N.meta_eth_len(m) == 14
+        assert m & N.META_L4_CSUM_OK
+        if v == 4:
+            assert m & N.META_IP_CSUM_OK
+        for name in SET["eth"] + SET[v] + SET[{17: 17, 6: 6.5}.get(p, 1)]:
+            assert np.array_equal(g[name], r[name]), (v, p, flen, name)
+        assert g["ether_type"] == (0x0800 if v == 4 else 0x86DD)
+        assert g["ip_length"] == (flen - 14 if v == 4 else flen - 54)
+        if p == 17:
+            assert g["udp_length_or_window"] == flen - 14 - (20 if v == 4 else 40)
+        assert f[flen - len(pay):] == pay
+
+
 def test_reference_unit_test_values():
     """echo_reply.rs:231-255 push_and_set_echo_reply: header_len 4, payload
     4 (the body) then 4 + 10 after set_data(&[0; 10]), type EchoReply, code
