@@ -166,6 +166,29 @@ class TxFramesOut(ctypes.Structure):  # cgtx_frames_out
     ]
 
 
+# The segment-routing extension, include/capsule_gpu_srv6.h (checked by
+# tests/test_abi_srv6.py): separately versioned, same library.
+SR_ABI_VERSION = 1
+SR_EXPORTS = ["cgsr_apply", "cgsr_status_str", "cgsr_abi_version"]
+SR_OP = {"NONE": 0, "ENCAP": 1, "SET": 2, "END": 3, "DECAP": 4}
+SR_P_SET_DST, SR_P_FINAL_FROM_PACKET = 1, 2
+# per-packet statuses: PKT below 64, these from 64 up
+SR_STATUS = {"BAD_OP": 64, "BAD_POLICY": 65, "NOT_ROUTING": 66, "NO_SEGMENTS_LEFT": 67,
+             "BAD_SEGMENTS_LEFT": 68}
+SR_POLICY_FIELDS = [("seg_first", "<u4"), ("n_segments", "u1"), ("segments_left", "u1"),
+                    ("tag", "<u2"), ("flags", "u1"), ("pad", "u1", (7,))]  # cgsr_policy
+SR_POLICY_SIZE = 16
+
+
+class SrPolicies(ctypes.Structure):  # cgsr_policies
+    _fields_ = [
+        ("policy", ctypes.c_void_p),
+        ("n_policies", ctypes.c_uint32),
+        ("segments", ctypes.c_void_p),
+        ("n_segments_total", ctypes.c_uint32),
+    ]
+
+
 _libs = {}
 
 
@@ -243,7 +266,14 @@ def lib(test=False):
     L.cgtx_hdr_defaults.argtypes = [u32, u32, vp]
     L.cgtx_build_batch.restype = i32
     L.cgtx_build_batch.argtypes = [vp, vp, u32, P(TxPayload), P(TxFramesOut), u32, vp]
-    if L.cgpu_abi_version() != ABI_VERSION or L.cgtx_abi_version() != TX_ABI_VERSION:
+    L.cgsr_abi_version.restype = i32
+    L.cgsr_status_str.restype = ctypes.c_char_p
+    L.cgsr_status_str.argtypes = [i32]
+    L.cgsr_apply.restype = i32
+    L.cgsr_apply.argtypes = [vp, P(Batch), vp, vp, P(SrPolicies), u32, u32, vp, ctypes.c_uint64,
+                             vp, vp, vp, vp]
+    if (L.cgpu_abi_version() != ABI_VERSION or L.cgtx_abi_version() != TX_ABI_VERSION
+            or L.cgsr_abi_version() != SR_ABI_VERSION):
         raise RuntimeError(f"capsule_amd: {path.name} ABI version mismatch")
     _libs[test] = L
     return L

@@ -149,6 +149,9 @@ class Batch:
     def replace(self, fn):
         return Replace(self, fn)
 
+    def srv6(self, policies, fn, flags=None, room=2048):
+        return Srv6(self, policies, fn, flags, room)
+
     def emit(self, tx):
         return Emit(self, tx)
 
@@ -334,6 +337,37 @@ class FilterMap(Batch):
         if st is not None:
             ab = d == ABORT
             b.status[idx[ab]] = st.to(torch.uint8)[ab]
+        return b
+
+
+class Srv6(Batch):
+    """SRv6 edits (packets.srv6): fn(burst of the Act packets) returns device
+    tensors (op u8, policy_idx i32 or None) per packet; every packet whose
+    edit fails aborts with that status (the `?` of `push::<SegmentRouting>`,
+    `set_segments`, `remove`), the rest continue as the rewritten burst (a
+    new arena; packets that were not Act are copied unchanged)."""
+
+    def __init__(self, upstream, policies, fn, flags, room):
+        super().__init__(upstream.ctx, upstream)
+        self.policies, self.fn, self.flags, self.room = policies, fn, flags, room
+
+    def apply(self, b):
+        idx, sub = _acting(b)
+        if idx is None:
+            return b
+        op, pidx = self.fn(sub)
+        dev = idx.device
+        op_all = torch.zeros(b.n, dtype=torch.uint8, device=dev)
+        op_all[idx] = op.to(torch.uint8)
+        pidx_all = None
+        if pidx is not None:
+            pidx_all = torch.zeros(b.n, dtype=torch.int32, device=dev)
+            pidx_all[idx] = pidx.to(torch.int32)
+        out, st = packets.srv6(self.ctx, b.batch, op_all, pidx_all, self.policies,
+                               flags=self.flags, room=self.room)
+        _abort(b, idx, st[idx])
+        b.batch = out
+        b.parsed = None
         return b
 
 

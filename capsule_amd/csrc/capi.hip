@@ -20,6 +20,7 @@
 
 #include "capsule_gpu.h"
 #include "capsule_gpu_tx.h"
+#include "capsule_gpu_srv6.h"
 #include "kernels.hpp"
 
 // How a nat64 call orders itself behind the map's previous call: it waits
@@ -1841,6 +1842,63 @@ int cgtx_build_batch(cgpu_ctx *ctx, const cgpu_hdr_record *rec, uint32_t n,
   a.status = out->status;
   a.room = room;
   hipError_t e = cgpu::launch_build(a, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e);
+  return ok();
+}
+
+// ---- segment-routing extension (include/capsule_gpu_srv6.h) ----------------
+int cgsr_abi_version(void) { return CGSR_ABI_VERSION; }
+
+const char *cgsr_status_str(int s) {
+  switch (s) {
+    case CGSR_BAD_OP: return "no such operation";
+    case CGSR_BAD_POLICY: return "no such policy, or a segment list it cannot set";
+    case CGSR_NOT_ROUTING: return "not an IPv6 routing packet.";
+    case CGSR_NO_SEGMENTS_LEFT: return "no segments left";
+    case CGSR_BAD_SEGMENTS_LEFT: return "segments left past the last entry";
+    default: return s >= 0 && s < CGPU_PKT_STATUS_COUNT ? cgpu_pkt_status_str(s) : "unknown status";
+  }
+}
+
+int cgsr_apply(cgpu_ctx *ctx, const cgpu_batch *in, const uint8_t *op, const uint32_t *policy_idx,
+               const cgsr_policies *pol, uint32_t flags, uint32_t room, uint8_t *out_arena,
+               uint64_t out_arena_len, const uint32_t *out_off, uint16_t *out_len,
+               uint8_t *status, void *stream) {
+  if (!ctx || !in || !in->arena || !in->off || !in->len || !op || !out_arena || !out_off ||
+      !out_len)
+    return fail(CGPU_EINVAL);
+  if (policy_idx && (!pol || !pol->policy || !pol->segments)) return fail(CGPU_EINVAL);
+  if (in->n > CGPU_MAX_BATCH || room == 0u || room > 65536u) return fail(CGPU_EINVAL);
+  if (in->arena_len > 0xffff0000ull || out_arena_len > 0xffff0000ull) return fail(CGPU_EINVAL);
+  if (pol && pol->n_segments_total > 0x0fff0000u) return fail(CGPU_EINVAL);
+  {
+    const uintptr_t o = (uintptr_t)out_arena, p = (uintptr_t)in->arena;
+    if (o < p + in->arena_len && p < o + out_arena_len) return fail(CGPU_EINVAL);
+  }
+  if (in->n == 0) return ok();
+  DeviceGuard dg(ctx->device);
+  if (!dg.ok()) return fail(CGPU_ENODEV);
+  const bool has_pol = policy_idx && pol;
+  cgpu::Srv6Args a{};
+  a.in_arena = in->arena;
+  a.in_arena_len = (uint32_t)in->arena_len;
+  a.in_off = in->off;
+  a.in_len = in->len;
+  a.n = in->n;
+  a.op = op;
+  a.policy_idx = has_pol ? policy_idx : nullptr;
+  a.policy = has_pol ? pol->policy : nullptr;
+  a.n_policies = has_pol ? pol->n_policies : 0u;
+  a.segments = has_pol ? pol->segments : nullptr;
+  a.n_segments_total = has_pol ? pol->n_segments_total : 0u;
+  a.flags = flags;
+  a.room = room;
+  a.out_arena = out_arena;
+  a.out_arena_len = (uint32_t)out_arena_len;
+  a.out_off = out_off;
+  a.out_len = out_len;
+  a.status = status;
+  hipError_t e = cgpu::launch_srv6(a, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(e);
   return ok();
 }

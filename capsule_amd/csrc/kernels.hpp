@@ -243,4 +243,27 @@ struct BuildArgs {
 };
 hipError_t launch_build(const BuildArgs &a, hipStream_t s);
 
+// ---- cgsr_apply (srv6.hip) -------------------------------------------------
+struct Srv6Args {
+  const uint8_t *in_arena;
+  uint32_t in_arena_len;
+  const uint32_t *in_off;
+  const uint16_t *in_len;
+  uint32_t n;
+  const uint8_t *op;
+  const uint32_t *policy_idx;  // nullptr: every ENCAP / SET is BAD_POLICY
+  const void *policy;          // cgsr_policy [n_policies]
+  uint32_t n_policies;
+  const uint8_t *segments;
+  uint32_t n_segments_total;
+  uint32_t flags;  // CGPU_F_ACCEPT_UDP | _TCP | _ICMP
+  uint32_t room;
+  uint8_t *out_arena;
+  uint32_t out_arena_len;
+  const uint32_t *out_off;
+  uint16_t *out_len;
+  uint8_t *status;  // optional
+};
+hipError_t launch_srv6(const Srv6Args &a, hipStream_t s);
+
 }  // namespace cgpu

@@ -788,3 +788,84 @@ def build(ctx, records, payload=None, out_arena=None, out_off=None, room=2048, s
     if stream is not None:
         records.record_stream(stream)
     return PacketBatch(out_arena, out_off, out_len), status
+
+
+# ---- SRv6 edits (include/capsule_gpu_srv6.h) ---------------------------------
+class Srv6Policies:
+    """`cgsr_policies` on the device: `policy` uint8 [n, 16] (cgsr_policy
+    records), `segments` uint8 [total, 16] (wire order) and the longest
+    list's length."""
+
+    def __init__(self, policy, segments, max_n):
+        self.policy, self.segments, self.max_n = policy, segments, max_n
+
+    def cstruct(self):
+        p = N.SrPolicies()
+        p.policy, p.n_policies = self.policy.data_ptr(), self.policy.shape[0]
+        p.segments, p.n_segments_total = self.segments.data_ptr(), self.segments.shape[0]
+        return p
+
+
+def srv6_policies(policies, device):
+    """[(segments, segments_left, tag, flags)] -> Srv6Policies.  segments: a
+    list of 16-byte strings (segments[0] is the final one, srh.rs:456-470);
+    flags: N.SR_P_SET_DST | N.SR_P_FINAL_FROM_PACKET."""
+    rec = np.zeros(len(policies), np.dtype(N.SR_POLICY_FIELDS))
+    segs = []
+    for i, (sg, sl, tag, fl) in enumerate(policies):
+        if not 1 <= len(sg) <= 127 or any(len(x) != 16 for x in sg):
+            raise ValueError("a policy has 1..127 segments of 16 bytes")
+        rec[i] = (len(segs), len(sg), sl, tag, fl, 0)
+        segs.extend(sg)
+    pol = torch.from_numpy(rec.view(np.uint8).reshape(-1, N.SR_POLICY_SIZE)).to(device)
+    arena = torch.from_numpy(np.frombuffer(b"".join(segs), np.uint8).reshape(-1, 16).copy())
+    return Srv6Policies(pol, arena.to(device), max((len(p[0]) for p in policies), default=0))
+
+
+def srv6(ctx, batch, op, policy_idx, policies, flags=None, room=2048, out=None, stream=None):
+    """`cgsr_apply`: per packet, op[i] (N.SR_OP: ENCAP = Ipv6::push::<
+    SegmentRouting> + set_segments, SET = set_segments, END = the next
+    segment becomes the destination, DECAP = remove, NONE = a copy) with
+    policy policies[policy_idx[i]], then reconcile_all() -- one launch.
+
+    op: device uint8 [n]; policy_idx: device int32 [n] or None; policies: a
+    Srv6Policies or None; flags: the accepted L4 types (N.F_ACCEPT_UDP |
+    _TCP | _ICMP, default UDP | TCP).  out: (out_arena, out_off) to write
+    into; by default frame i gets a slot of len + 8 + 16 * max_n bytes rounded
+    up to 64.  Returns (PacketBatch, status u8 [n]): 0, a N.PKT value or a
+    N.SR_STATUS value; a packet that is not edited has len 0.  Asynchronous
+    on `stream`."""
+    n, dev = batch.n, batch.arena.device
+    if op.dtype != torch.uint8 or op.numel() != n:
+        raise TypeError("op: uint8 [n]")
+    if policy_idx is not None and (policy_idx.dtype != torch.int32 or policy_idx.numel() != n):
+        raise TypeError("policy_idx: int32 [n]")
+    if policy_idx is not None and policies is None:
+        raise ValueError("policy_idx needs the policies it indexes")
+    if out is None:
+        grow = 8 + 16 * (policies.max_n if policies is not None else 0)
+        slot = ((batch.len.to(torch.int64) & 0xFFFF) + grow + 63) // 64 * 64
+        end = torch.cumsum(slot, 0)
+        total = int(end[-1].item()) if n else 0
+        if total > 0xFFFF0000:
+            raise ValueError("out arena past 4 GiB: pass out")
+        out_off = end - slot
+        out_off = torch.where(out_off >= 1 << 31, out_off - (1 << 32), out_off).to(torch.int32)
+        out_arena = torch.empty(max(total, 64), dtype=torch.uint8, device=dev)
+    else:
+        out_arena, out_off = out
+    out_len = torch.empty(n, dtype=torch.int16, device=dev)
+    status = torch.empty(n, dtype=torch.uint8, device=dev)
+    cb = batch.cbatch()
+    cp = policies.cstruct() if policies is not None else None
+    rc = ctx.L.cgsr_apply(ctx.handle, ctypes.byref(cb), _ptr(op), _ptr(policy_idx),
+                          ctypes.byref(cp) if cp is not None else None,
+                          N.F_ACCEPT_UDP | N.F_ACCEPT_TCP if flags is None else flags, room,
+                          _ptr(out_arena), out_arena.numel(), _ptr(out_off), _ptr(out_len),
+                          _ptr(status), _stream_handle(stream))
+    N.check(rc, "cgsr_apply")
+    if stream is not None:
+        for t in (batch.arena, batch.off, batch.len, op, policy_idx):
+            if t is not None:
+                t.record_stream(stream)
+    return PacketBatch(out_arena, out_off, out_len), status
